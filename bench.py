@@ -133,6 +133,43 @@ def one_step(model, ts, bitfield, batch, mean_count, next_batch=None):
     return ts.step(o, d, gt, noises=noise, next_rays=nxt)
 
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: elements kept of a larger array (a fixed, seeded sample)
+DUMP_BUDGET = 64 << 20         # --dump-outputs: bytes of all files together
+
+
+def dump_outputs(out_dir, loss, model, ts):
+    """--dump-outputs DIR: what the timed path handed its caller after the last timed step, as DIR/<name>.npy (float32).
+    loss, mse, wavelet_reg: the step's returned scalars; image, weights_sum, depth: its per-ray renders (TrainStep.last);
+    param.<name>: every trained parameter after the step's optimiser pass (deferred part applied); buffer.density_grid:
+    the occupancy grid the step's refreshes maintain.  An array of more than DUMP_SAMPLE elements is stored as the
+    flattened values at DUMP_SAMPLE sorted indices drawn from a generator seeded with crc32(<name>) -- the same
+    positions in every run and build -- so that two builds can be compared file for file."""
+    import zlib
+    arrays = {"loss": loss}
+    for key, name in (("mse", "mse"), ("wavelet_reg", "wavelet_reg"), ("image", "image"), ("ws", "weights_sum"),
+                      ("depth", "depth")):
+        if torch.is_tensor(ts.last.get(key)):
+            arrays[name] = ts.last[key]
+    for n, p in model.named_parameters():
+        arrays["param." + n] = p
+    arrays["buffer.density_grid"] = model.density_grid
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        shape = tuple(t.shape)
+        if flat.numel() > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            shape = (DUMP_SAMPLE,)
+        a = flat.float().cpu().numpy().reshape(shape)
+        total += a.nbytes
+        assert total <= DUMP_BUDGET, f"--dump-outputs: more than {DUMP_BUDGET >> 20} MB"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def cpu_baseline(workload):
     """Reference operator set on the host cores (oracle/torch_baseline.py), BASELINE.md section 3's procedure: the dense
     part (plane rebuild, its backward, regulariser, Adam) at the FULL plane size, the per-ray part on a reduced ray count
@@ -653,7 +690,14 @@ def main():
                          "TrainStep(single_rank_collectives=True) -- every collective of the sharded step is issued (RCCL "
                          "kernels on its own stream); what the exchange's launches cost without any wire")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # a rocprofv3 --pmc pass of pmc_traffic_live
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, renders, updated parameters; "
+                         "a seeded sample of the large arrays) as DIR/<name>.npy, float32, 64 MB at most.  The steps "
+                         "then reduce the plane gradient in sample-id order (TrainStep(deterministic=True)): the same "
+                         "bits every run, at the cost of an ordering pass per step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pmc_child or args.single_rank_collectives:
         args.no_extras = args.no_cpu_baseline = True
 
@@ -666,6 +710,9 @@ def main():
         local_rank = 0
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
+    # the density-grid refreshes draw their jitter and cell picks from torch's generators: seeded, so that every run
+    # with the same arguments sees the same inputs (the rays, the field's initial state and the march noise are seeded)
+    torch.manual_seed(rank)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if args.backend == "nccl":
@@ -692,8 +739,13 @@ def main():
 
     global GRAPH
     GRAPH = world == 1 and args.graph
+    # --dump-outputs: every tile list of the plane-gradient reduction ordered by sample id (TrainStep(deterministic=True)),
+    # so that the fp32 summation order -- by default the arrival order of the tile sort's atomics -- and with it every
+    # bit of every step is the same from run to run; the Adam steps after it would otherwise carry those last-bit
+    # differences into visible ones.  The ordering pass costs time: take step times from runs without the flag.
     model, ts, bitfield, N = build(args.workload, device, args.dist_mode if (world > 1 or lone) else None,
-                                   **({"single_rank_collectives": True} if lone else {}))
+                                   **({"single_rank_collectives": True} if lone else {}),
+                                   **({"deterministic": True} if args.dump_outputs else {}))
     if os.environ.get("TNL_CLIP_FAR"):      # A/B: the in-order march of refresh steps clipped to the occupied box (default on)
         ts.clip_far_in_order = os.environ["TNL_CLIP_FAR"] != "0"
     n_global = N * world
@@ -756,7 +808,7 @@ def main():
     t0 = time.perf_counter()
     flushes0, deferred0 = ts.deferred_flushes, ts.deferred_steps
     for i in range(args.steps):
-        one_step(model, ts, bitfield, batches[(args.warmup + i) % nb], mean_count, batches[(args.warmup + i + 1) % nb])
+        loss = one_step(model, ts, bitfield, batches[(args.warmup + i) % nb], mean_count, batches[(args.warmup + i + 1) % nb])
     # the optimiser work TrainStep deferred during these steps (coefficients outside the occupancy window's footprint,
     # replayed in one pass per flush) belongs to them: it is done before the clock stops
     ts.flush_deferred()
@@ -769,6 +821,14 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    if args.dump_outputs:
+        # after the clock: the last timed step's results, before any later pass changes the model
+        if world > 1 or lone:
+            ts.sync_sharded_parameters()          # a collective: every rank's slices of the coefficients
+        if rank == 0:
+            nbytes = dump_outputs(args.dump_outputs, loss, model, ts)
+            print(f"bench.py: outputs of the last timed step ({nbytes / 2 ** 20:.1f} MB) -> {args.dump_outputs}",
+                  file=sys.stderr)
 
     timed_flushes, timed_deferred = ts.deferred_flushes - flushes0, ts.deferred_steps - deferred0
     captured_steps = None if not ts.graph else {

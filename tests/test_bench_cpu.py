@@ -34,3 +34,48 @@ def test_every_profiled_kernel_of_a_section_is_owned_by_it():
     assert not bench.section_owns("adam_coef", "k_adam_l1_catchup")
     # hidden 128's two-launch backward (templated name, csrc/field_bwd.hip) belongs to the same section
     assert bench.section_owns("field_bwd", _short("void (anonymous namespace)::k_field_bwd<48, 128, 1>(Args)"))
+
+
+def test_dump_outputs_writes_the_same_sample_every_time(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 .npy per output, arrays above DUMP_SAMPLE elements as the values at
+    fixed seeded positions -- the same positions in every run, so two builds compare file for file."""
+    import numpy as np
+    import torch
+    import bench
+    from trinerflet_amd import synthetic
+    from trinerflet_amd.nerf.network import NeRFNetwork
+
+    class _Step:
+        pass
+
+    def model():
+        m = NeRFNetwork(encoding="triplane_wavelet", bound=1.5, cuda_ray=True, density_thresh=10, hidden_dim=64,
+                        hidden_dim_color=64, triplane_channels=16, triplane_resolution=256, triplane_wavelet_levels=4,
+                        wavelet_type="bior6.8")
+        synthetic.init_field_parameters(m, seed=0)
+        return m
+
+    ts = _Step()
+    rng = np.random.default_rng(0)
+    ts.last = {"mse": torch.tensor(0.25), "wavelet_reg": torch.tensor(0.5), "image": torch.from_numpy(rng.random((64, 3))),
+               "ws": torch.from_numpy(rng.random(64)), "depth": torch.from_numpy(rng.random(64)), "M": 7}
+    dumps = []
+    for k in range(2):
+        m = model()
+        out = tmp_path / f"d{k}"
+        nbytes = bench.dump_outputs(str(out), torch.tensor(0.75), m, ts)
+        files = {f.name[:-4]: np.load(f) for f in out.iterdir()}
+        assert nbytes == sum(a.nbytes for a in files.values()) <= bench.DUMP_BUDGET
+        assert all(a.dtype == np.float32 for a in files.values())
+        dumps.append(files)
+    a, b = dumps
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert float(a["loss"]) == 0.75 and a["image"].shape == (64, 3) and "M" not in a
+    assert {"param." + n for n, _ in m.named_parameters()} | {"buffer.density_grid"} <= set(a)
+    assert a["param.encoder.planes_features"].shape == (3, 16, 64, 64)       # small: whole
+    big = "param.encoder.planes_features_wavelet_coefs.1"                     # 3 x 16 x 3 x 128^2: sampled
+    full = dict(m.named_parameters())[big[len("param."):]].detach().reshape(-1).numpy()
+    assert full.size > bench.DUMP_SAMPLE and a[big].shape == (bench.DUMP_SAMPLE,)
+    import zlib
+    idx = np.sort(np.random.default_rng(zlib.crc32(big.encode())).integers(0, full.size, bench.DUMP_SAMPLE))
+    assert np.array_equal(a[big], full[idx])

@@ -75,6 +75,46 @@ def test_default_bench_line_is_short_flat_and_last(cuda, tmp_path):
             assert any(k.startswith("k_field_bwd") for k in fe["traffic_per_kernel"]), fe["traffic_per_kernel"]
 
 
+def test_dump_outputs_of_the_last_timed_step(cuda, tmp_path):
+    """--dump-outputs DIR: after the timed steps, the last one's loss, renders and updated parameters land in DIR as float32
+    .npy files (the large arrays as a seeded sample), 64 MB at most; --steps is the number of timed steps of the line.  Two
+    runs with the same arguments write the same arrays: the inputs are seeded and the steps reduce in a fixed order (only
+    the loss scalars, summed by float atomics, may differ in the last bits)."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"dump{k}"
+        env = dict(os.environ, TNL_BENCH_DETAIL=str(tmp_path / "bench_detail.json"))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup",
+                            "0", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        assert all(f.suffix == ".npy" for f in out.iterdir())
+        runs.append({f.name[:-4]: np.load(f) for f in out.iterdir()})
+    files, again = runs
+    assert set(files) == set(again)
+    for k in files:
+        if k in ("loss", "mse", "wavelet_reg"):
+            np.testing.assert_allclose(again[k], files[k], rtol=1e-5, atol=0, err_msg=k)
+        else:
+            assert np.array_equal(again[k], files[k]), k
+    need = {"loss", "mse", "wavelet_reg", "image", "weights_sum", "depth", "param.encoder.planes_features",
+            "param.encoder.planes_features_wavelet_coefs.1", "param.sigma_net.0.weight", "param.color_net.2.weight",
+            "buffer.density_grid"}
+    assert need <= set(files), sorted(files)
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["image"].shape == (4096, 3) and files["weights_sum"].shape == (4096,)
+    assert files["param.encoder.planes_features"].shape == (3, 16, 64, 64)
+    assert files["param.encoder.planes_features_wavelet_coefs.1"].shape == (1 << 20,)      # 3 x 16 x 3 x 128^2: sampled
+    for k in ("loss", "mse", "image", "param.encoder.planes_features", "param.encoder.planes_features_wavelet_coefs.1",
+              "param.sigma_net.0.weight"):
+        assert np.isfinite(files[k]).all(), k
+    assert float(files["loss"]) > 0
+
+
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_two_ranks_on_one_device(cuda, scaling):
     """The N > 1 code path of bench.py itself (ray shards, slice-sharded dense work, collectives, max-over-ranks

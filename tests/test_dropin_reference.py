@@ -5,7 +5,8 @@ trinerflet_amd.install_dropin() the import block of reconstruction/main_nerf.py:
 does from the README's command lines, the reference's Trainer accepts it, and the reference's own
 aux_libs/raymarching/raymarching.py / shencoder/sphere_harmonics.py bind `_raymarching` / `_shencoder` unchanged.
 
-Skipped where /root/reference does not exist (the GPU box).  Every check runs in a child process: it rewires
+Skipped where /root/reference does not exist (the GPU box, a clean checkout); the wrapper-binding and `--ff` checks run
+everywhere against recorded reference data in test_dropin_fixtures.py.  Every check runs in a child process: it rewires
 sys.modules / sys.path.  Third-party packages the reference imports at module level but that this image lacks (cv2,
 tensorboardX, mcubes, ...) are replaced by empty placeholder modules -- none is touched by the code under test."""
 import os

@@ -14,10 +14,16 @@ occupancy r=0.8 re-imposed after each grid refresh (the refresh itself runs and 
 Weak scaling: every rank processes its own 60 000 rays per step; value = rays of all ranks / max-rank time.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` -- the section of the step with the
-largest per-step time (found by an instrumented pass before the timed steps, then timed with HIP events inside them),
-its binding roof (HBM bytes or MFMA flops, whichever takes longer at peak), `roofline.top` = the three longest
-sections with algorithmic bytes / flops, fraction and counter traffic, the step's actual traffic, this box's measured
-copy bandwidth -- and `cpu_baseline`.  `config.trajectory`: 512 steps from an untrained grid (tools/trajectory.py).
+largest per-step time (found by an instrumented pass of the set-up, then timed with HIP events inside the timed steps)
+and its binding roof (HBM bytes or MFMA flops, whichever takes longer at peak).  A plain run does nothing else: set-up,
+warm-up, the timed steps, --dump-outputs, the line.
+
+--full adds what takes runs of its own, after the timed steps: every section's time (an instrumented pass, and one
+without the side work), two whole density-grid periods, `roofline.top` = the three longest sections with algorithmic
+bytes / flops, fraction and counter traffic (live rocprofv3 passes), the step's actual traffic, this box's measured
+copy bandwidth, the secondary figures (other workloads and precisions, inference, the reference's loop on the drop-in
+modules, `config.trajectory`: 512 steps from an untrained grid, tools/trajectory.py) and `cpu_baseline`; the whole
+record goes to a side file (TNL_BENCH_DETAIL, default bench_detail.json beside this script).
 """
 import argparse
 import gc
@@ -219,7 +225,8 @@ def pmc_traffic_live(workload):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(td, counter)
             cmd = [prof, "--pmc", counter, "-d", out, "--output-format", "csv", "--", sys.executable,
-                   os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "2", "--warmup", "0", "--pmc-child"]
+                   os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "2", "--warmup", "0", "--full",
+                   "--pmc-child"]
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=td)
             except Exception as e:                                   # noqa: BLE001
@@ -595,10 +602,10 @@ def _num(v, nd=4):
     return v
 
 
-def compact_line(out):
-    """The ONE stdout line of the contract, derived from the full record `out` (which goes to gpurun_out/bench_detail.json):
-    the contract's keys, a flat `config` of scalars, `roofline` (scalars + a 3-entry `top` of scalars) and `cpu_baseline`
-    (scalars).  Kept below 4 KB so that any driver-side line buffer holds it."""
+def compact_line(out, detail=None):
+    """The ONE stdout line of the contract, derived from the record `out` (with --full written whole to the side file
+    `detail`): the contract's keys, a flat `config` of scalars, `roofline` (scalars; with --full + a 3-entry `top` of
+    scalars) and, with --full, `cpu_baseline` (scalars).  Kept below 4 KB so that any driver-side line buffer holds it."""
     cfg, rf = out["config"], out["roofline"]
     flat = {"workload": cfg["workload"]}
     for k in ("rays_per_step_per_gpu", "rays_per_step_global", "samples_per_step_per_gpu", "sample_budget_M", "samples_per_sec",
@@ -634,10 +641,8 @@ def compact_line(out):
         flat[f"{wl}_ms_per_step"] = rep.get("ms_per_step")
     for k, v in (cfg.get("sections_ms") or {}).items():
         flat["ms_" + k] = _num(v)
-    flat["detail"] = "gpurun_out/bench_detail.json"
-    top = [{"section": e["section"], "ms": e["ms_per_step"], "bound": e["bound"], "achieved": _num(e["achieved"]),
-            "unit": e["unit"], "frac": _num(e["frac"]), "traffic_over_algorithmic": e.get("traffic_over_algorithmic")}
-           for e in rf["top"]]
+    if detail is not None:
+        flat["detail"] = detail
     roofline = {k: _num(rf.get(k)) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
     if roofline["achieved"] is not None and roofline["peak"]:
         roofline["frac"] = roofline["achieved"] / roofline["peak"]          # exactly A / P of the printed A and P
@@ -646,7 +651,11 @@ def compact_line(out):
                      "algorithmic_bytes_per_launch": _num(rf["algorithmic_bytes_per_launch"]),
                      "algorithmic_flops_per_launch": _num(rf["algorithmic_flops_per_launch"]),
                      "alone_frac": None if not rf.get("alone") else rf["alone"]["frac"],
-                     "measured_copy_GB/s": rf.get("measured_copy_GB/s"), "top": top})
+                     "measured_copy_GB/s": rf.get("measured_copy_GB/s")})
+    if rf.get("top") is not None:
+        roofline["top"] = [{"section": e["section"], "ms": e["ms_per_step"], "bound": e["bound"],
+                            "achieved": _num(e["achieved"]), "unit": e["unit"], "frac": _num(e["frac"]),
+                            "traffic_over_algorithmic": e.get("traffic_over_algorithmic")} for e in rf["top"]]
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                 "scaling", "vs_baseline", "dtype", "data")}
     line["config"] = flat
@@ -671,7 +680,12 @@ def main():
     ap.add_argument("--workload", default="base", choices=sorted(WORKLOADS))
     ap.add_argument("--dist-mode", default="auto", choices=["auto", "sharded", "allreduce"],
                     help="auto: mode and exchange bands from the cost model (distributed.plan_exchange, TNL_XGMI_GBS)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: every section's time, whole "
+                         "density-grid periods, the secondary figures, live counter traffic and the CPU baseline (see "
+                         "--no-extras, --no-cpu-baseline); the whole record goes to a side file (TNL_BENCH_DETAIL, default "
+                         "bench_detail.json beside this script)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--graph", action="store_true",
                     help="the steady-state steps of a density-grid period replayed as captured HIP graphs (TrainStep(graph=True)). "
                          "Off by default: measured at base, natural loop, steady positions 3.50 ms eager vs 3.61-3.68 ms "
@@ -680,11 +694,12 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, the measured configuration); gloo only to dry-run the N>1 code on one GPU")
     ap.add_argument("--same-device", action="store_true", help="all ranks on cuda:0 (dry-run with --backend gloo)")
-    ap.add_argument("--sections", action="store_true", help="print a per-section time breakdown to stderr")
+    ap.add_argument("--sections", action="store_true", help="with --full: print a per-section time breakdown to stderr")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank its own 60 000 rays per step; strong: the 60 000 rays of a step split over the ranks")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary figures (whole-plane / fp32-plane step times, inference, live PMC traffic)")
+                    help="with --full: skip the secondary figures (whole-plane / fp32-plane step times, inference, live PMC "
+                         "traffic)")
     ap.add_argument("--single-rank-collectives", action="store_true",
                     help="one GPU, but the N-GPU code path: a process group of ONE rank over --backend and "
                          "TrainStep(single_rank_collectives=True) -- every collective of the sharded step is issued (RCCL "
@@ -698,6 +713,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.sections and not args.full:
+        ap.error("--sections prints the instrumented pass of --full: add --full")
     if args.pmc_child or args.single_rank_collectives:
         args.no_extras = args.no_cpu_baseline = True
 
@@ -838,37 +855,43 @@ def main():
                 "position; bit-identical to the eager launches (tests/test_graph_step_gpu.py)"}
     # the dominant section's time from the HIP events recorded inside the timed region ...
     dom_ms = ts.section_times().get(dominant, float("nan"))
-    # ... and every section's, for the other figures, from an instrumented pass AFTER it (not part of the K steps)
-    ts.section_events, ts.section_names = [], None
-    for i in range(min(args.steps, 16)):
-        j = args.warmup + args.steps + i
-        one_step(model, ts, bitfield, batches[j % nb], mean_count, batches[(j + 1) % nb])
-    torch.cuda.synchronize()
-    sec = ts.section_times()
-    sec_instrumented_dominant = sec.get(dominant)
+    sec = {} if dom_ms != dom_ms else {dominant: dom_ms}
+    sec_alone, sec_instrumented_dominant, whole_periods_ms = {}, None, None
     dom_timing = "HIP events on the launch stream inside the timed steps"
-    if dom_ms == dom_ms:
-        sec[dominant] = dom_ms
-    else:       # captured steps: see above
-        dom_ms = sec_instrumented_dominant
-        dom_timing = ("HIP events on the launch stream in the instrumented eager pass of min(K, 16) steps right after the timed "
-                      "region -- the timed region replays captured graphs, inside which nothing can be timed (an event "
-                      "recorded during a capture has no elapsed time on HIP)")
-    # the same sections with NOTHING beside them (the next batch's march + tile sort in order on the launch stream
-    # instead of on the side stream): what each kernel does alone, for `roofline.alone` and `kernels[*].alone_ms`
-    ts.section_events, ts.section_names = [], None
-    ts._drop_prefetch()
-    ts.overlap_march = False
-    for i in range(min(args.steps, 8)):
-        j = args.warmup + args.steps + 16 + i
-        one_step(model, ts, bitfield, batches[j % nb], mean_count, None)
-    torch.cuda.synchronize()
-    sec_alone = ts.section_times()
-    ts.overlap_march = not os.environ.get("TNL_NO_OVERLAP")
-    ts.section_events = None
-    # the driver's K = 20 timed steps hold one grid refresh (1 / 20) where a long run holds one per 16 steps: the same
-    # loop over 32 steps = two whole density-grid periods, refreshes and replays inside (after the timed region)
-    whole_periods_ms = time_steps(model, ts, bitfield, batches, mean_count, 32, setup=0) * 1e3
+    if args.full:
+        # ... and every section's, for the other figures, from an instrumented pass AFTER it (not part of the K steps)
+        ts.section_events, ts.section_names = [], None
+        for i in range(min(args.steps, 16)):
+            j = args.warmup + args.steps + i
+            one_step(model, ts, bitfield, batches[j % nb], mean_count, batches[(j + 1) % nb])
+        torch.cuda.synchronize()
+        sec = ts.section_times()
+        sec_instrumented_dominant = sec.get(dominant)
+        if dom_ms == dom_ms:
+            sec[dominant] = dom_ms
+        else:       # captured steps: see above
+            dom_ms = sec_instrumented_dominant
+            dom_timing = ("HIP events on the launch stream in the instrumented eager pass of min(K, 16) steps right after the "
+                          "timed region -- the timed region replays captured graphs, inside which nothing can be timed (an "
+                          "event recorded during a capture has no elapsed time on HIP)")
+        # the same sections with NOTHING beside them (the next batch's march + tile sort in order on the launch stream
+        # instead of on the side stream): what each kernel does alone, for `roofline.alone` and `kernels[*].alone_ms`
+        ts.section_events, ts.section_names = [], None
+        ts._drop_prefetch()
+        ts.overlap_march = False
+        for i in range(min(args.steps, 8)):
+            j = args.warmup + args.steps + 16 + i
+            one_step(model, ts, bitfield, batches[j % nb], mean_count, None)
+        torch.cuda.synchronize()
+        sec_alone = ts.section_times()
+        ts.overlap_march = not os.environ.get("TNL_NO_OVERLAP")
+        ts.section_events = None
+        # the driver's K = 20 timed steps hold one grid refresh (1 / 20) where a long run holds one per 16 steps: the same
+        # loop over 32 steps = two whole density-grid periods, refreshes and replays inside (after the timed region)
+        whole_periods_ms = time_steps(model, ts, bitfield, batches, mean_count, 32, setup=0) * 1e3
+    elif dom_ms != dom_ms:
+        dom_ms = None
+        dom_timing = "not measured: the timed steps replayed captured graphs (--full times the section after them)"
     samples_per_step = float(np.mean(counts))
     acct = adam_accounting(ts, world)
     adam_bytes, n_launch, deferred_coefs, band_share = acct["adam_bytes"], acct["n_launch"], acct["deferred_coefs"], acct["band_share"]
@@ -905,7 +928,7 @@ def main():
             kernels[k]["alone_ms"] = a["ms_per_step"]
             kernels[k]["alone_frac"] = round(a["frac"], 4)
 
-    # ---- secondary figures, after the timed region (rank 0's GPU only; skipped by --no-extras and in multi-GPU runs)
+    # ---- secondary figures, after the timed region (--full; rank 0's GPU only; skipped by --no-extras and in multi-GPU runs)
     extras = {}
     # what the run used and what the cost model (trinerflet_amd.distributed.plan_exchange) predicts for
     # it: compare ms_predicted with ms_per_step of a multi-GPU run, ms_one_gpu with the one-GPU line
@@ -924,10 +947,10 @@ def main():
                                                 "note": "bounding window of the occupied cells per plane (r = 0.8 sphere): "
                                                         "the finest IDWT level, layout change, plane gradient and adjoint "
                                                         "touch only this window on the 15 of 16 steps without a grid refresh"}
-    pmc, pmc_src = None, "not collected (--no-extras or multi-GPU run)"
+    pmc, pmc_src = None, "not collected (a run without --full, --no-extras or a multi-GPU run)"
     copy_gbs = None
     plc = ts.placement
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         copy_gbs = copy_bandwidth(device)
         extras["inference"] = inference_figure(model, device)
         pmc, pmc_src = pmc_traffic_live(args.workload)
@@ -990,9 +1013,10 @@ def main():
                                 "plus 54 kB of MLP-gradient all-reduce and three scalars"}
             else:
                 wire = {"all_reduce_plane_grad_bytes": 2.0 * S_all * R * R * 4.0 * (world - 1) / world}
-        # the three longest sections, each with its binding roof and its counter traffic
-        ranked = sorted((k for k in kernels if kernels[k] is not None), key=lambda k: -kernels[k]["ms_per_step"])
-        top = []
+        # the three longest sections, each with its binding roof and its counter traffic (--full: every section is timed)
+        ranked = sorted((k for k in kernels if kernels[k] is not None), key=lambda k: -kernels[k]["ms_per_step"]) \
+            if args.full else []
+        top = [] if args.full else None
         for k in ranked[:3]:
             e = dict(kernels[k])
             tr = traffic_of(k)
@@ -1034,10 +1058,11 @@ def main():
                        "collectives": None if (world == 1 and not lone) else {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                                                                "bytes_on_the_wire": wire},
                        "samples_per_sec": samples_per_step * world * args.steps / elapsed,
-                       "ms_per_step_over_whole_periods": round(whole_periods_ms, 4),
-                       "whole_periods_note": "32 steps = two whole density-grid periods (2 refreshes + their replays of the "
-                                             "deferred pass), measured after the timed region: what a long run averages, "
-                                             "where the timed K steps hold K / 16 refreshes only on average",
+                       **({} if whole_periods_ms is None else {
+                           "ms_per_step_over_whole_periods": round(whole_periods_ms, 4),
+                           "whole_periods_note": "32 steps = two whole density-grid periods (2 refreshes + their replays of "
+                                                 "the deferred pass), measured after the timed region: what a long run "
+                                                 "averages, where the timed K steps hold K / 16 refreshes only on average"}),
                        # SURVEY.md 8(d)'s byte count of the REFERENCE's step (every coefficient rebuilt, differentiated and
                        # updated every step: (44 + e) P + M (12 C e + 48 C + 64) + 64 N) over this step's time
                        "survey_step": {"bytes": survey_bytes, "TB/s_equivalent": round(survey_bytes / (ms * 1e-3) / 1e12, 3),
@@ -1047,7 +1072,7 @@ def main():
                                                "fewer (occupancy window, live rectangles of the optimiser pass)"},
                        "step_actual_traffic": step_traffic,
                        "sections_ms": {k: round(v, 4) for k, v in sec.items()},
-                       "sections_note": f"{dominant}: HIP events inside the timed steps; the other sections: an "
+                       "sections_note": f"{dominant}: HIP events inside the timed steps; the other sections (--full): an "
                                         "instrumented pass after them (an event at every boundary costs 6-8 us)",
                        "kernels": kernels,
                        "captured_steps": captured_steps,
@@ -1065,7 +1090,8 @@ def main():
                          "traffic_source": pmc_src,
                          "algorithmic_bytes_per_launch": spec[dominant]["bytes"] / n_dom,
                          "algorithmic_flops_per_launch": spec[dominant]["flops"] / n_dom,
-                         "avg_launch_ms": dom_ms / n_dom, "launches_per_step": n_dom, "timing": dom_timing,
+                         "avg_launch_ms": None if dom_ms is None else dom_ms / n_dom, "launches_per_step": n_dom,
+                         "timing": dom_timing,
                          "per_step": {"algorithmic_bytes": spec[dominant]["bytes"], "algorithmic_flops": spec[dominant]["flops"],
                                       "traffic_bytes": None if dtr is None else dtr["bytes"], "ms": dom_ms,
                                       "ms_instrumented_pass": sec_instrumented_dominant,
@@ -1087,22 +1113,25 @@ def main():
                                  "steps (the section's launches back to back, per launch = / launches_per_step); "
                                  "field_bwd includes its k_slab_reduce launch (weight-gradient slabs)"},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload)
         if args.sections:
             print(json.dumps(sec, indent=1), file=sys.stderr)
-        # The whole record (per-kernel tables, trajectory, inference, other workloads, notes) goes to a side file; the
-        # stdout line is the contract's keys only, flat and short (round 4's 22 KB line was not parsed by the driver).
-        detail_path = os.environ.get("TNL_BENCH_DETAIL", os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
-        try:
-            os.makedirs(os.path.dirname(detail_path), exist_ok=True)
-            with open(detail_path, "w") as fh:
-                json.dump(out, fh, indent=1)
-            print(f"bench.py: full record -> {detail_path}", file=sys.stderr)
-        except OSError as e:
-            print(f"bench.py: could not write {detail_path}: {e}", file=sys.stderr)
+        # --full: the whole record (per-kernel tables, trajectory, inference, other workloads, notes) goes to a side file;
+        # the stdout line is the contract's keys only, flat and short (round 4's 22 KB line was not parsed by the driver).
+        detail = None
+        if args.full:
+            detail_path = os.environ.get("TNL_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json"))
+            try:
+                os.makedirs(os.path.dirname(detail_path) or ".", exist_ok=True)
+                with open(detail_path, "w") as fh:
+                    json.dump(out, fh, indent=1)
+                print(f"bench.py: full record -> {detail_path}", file=sys.stderr)
+                detail = os.path.relpath(detail_path, ROOT) if detail_path.startswith(ROOT + os.sep) else detail_path
+            except OSError as e:
+                print(f"bench.py: could not write {detail_path}: {e}", file=sys.stderr)
         sys.stderr.flush()
-        line = json.dumps(compact_line(out))
+        line = json.dumps(compact_line(out, detail))
         assert len(line) < 4096, len(line)
         sys.stdout.write(line + "\n")
         sys.stdout.flush()

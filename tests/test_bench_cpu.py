@@ -3,6 +3,8 @@ import csv
 import glob
 import os
 import re
+import subprocess
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -79,3 +81,11 @@ def test_dump_outputs_writes_the_same_sample_every_time(tmp_path):
     import zlib
     idx = np.sort(np.random.default_rng(zlib.crc32(big.encode())).integers(0, full.size, bench.DUMP_SAMPLE))
     assert np.array_equal(a[big], full[idx])
+
+
+def test_sections_is_refused_without_full():
+    """--sections prints the instrumented pass after the timed steps, which only --full runs: without --full the
+    arguments are refused before anything touches a GPU."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sections"], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-1000:]

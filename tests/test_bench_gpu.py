@@ -1,4 +1,5 @@
-"""bench.py's output contract (one JSON line with the driver's keys + roofline + cpu_baseline) on the tiny workload."""
+"""bench.py's output contract (one JSON line with the driver's keys + roofline; with --full + cpu_baseline) on the tiny
+workload."""
 import json
 import os
 import subprocess
@@ -12,8 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_contract_line(cuda):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600,
-                       cwd=ROOT)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -40,14 +41,14 @@ def test_bench_prints_one_contract_line(cuda):
 
 
 def test_default_bench_line_is_short_flat_and_last(cuda, tmp_path):
-    """The line the DRIVER sees: the default command (extras, live PMC passes, CPU baseline), only the workload made tiny.
-    Round 4's default line was 22 KB and the driver recorded `parsed: null`; the contract line must stay below 4 KB, be the
-    last stdout line, hold scalars only below `config` / `cpu_baseline` / `roofline` (+ its 3-entry `top`), and the full
+    """The line of the --full command (extras, live PMC passes, CPU baseline), only the workload made tiny.  Round 4's
+    default line was 22 KB and the driver recorded `parsed: null`; the contract line must stay below 4 KB, be the last
+    stdout line, hold scalars only below `config` / `cpu_baseline` / `roofline` (+ its 3-entry `top`), and the full
     record must land in the side file."""
     detail = tmp_path / "bench_detail.json"
     env = dict(os.environ, TNL_BENCH_DETAIL=str(detail))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                        "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     out_lines = r.stdout.splitlines()
     line = out_lines[-1]
@@ -73,6 +74,39 @@ def test_default_bench_line_is_short_flat_and_last(cuda, tmp_path):
         assert e["traffic_over_algorithmic"] is not None and 0 < e["traffic_over_algorithmic"] < 3, e
         if e["section"] == "field_bwd":
             assert any(k.startswith("k_field_bwd") for k in fe["traffic_per_kernel"]), fe["traffic_per_kernel"]
+
+
+def test_plain_bench_run_does_only_the_headline(cuda, tmp_path):
+    """Without --full a run sets up, warms up, times its steps and prints the line: the contract's keys and the roofline
+    of the section timed inside the steps, nothing that takes runs of its own (no CPU baseline, no whole-period or
+    per-section passes, no secondary figures, no live counter traffic) and no side file."""
+    detail = tmp_path / "bench_detail.json"
+    env = dict(os.environ, TNL_BENCH_DETAIL=str(detail))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out_lines = r.stdout.splitlines()
+    line = out_lines[-1]
+    assert len(line) < 4096 and [l for l in out_lines if l.startswith("{")] == [line]
+    d = json.loads(line)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert k in d, k
+    assert d["metric"] == "train rays/sec (whole node)" and d["unit"] == "rays/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f16" and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and "top" not in d["roofline"] and d["roofline"]["traffic"] is None
+    cfg = d["config"]
+    assert all(not isinstance(v, (dict, list)) for v in cfg.values())
+    for k in ("ms_per_step_over_whole_periods", "fp32_planes_ms_per_step", "no_roi_ms_per_step", "detail",
+              "test_render_800x800_4096_steps_ms", "trajectory_512_steps_ms_per_step"):
+        assert k not in cfg, k
+    # the one section the line names is timed inside the timed steps, and only it
+    rf = d["roofline"]
+    assert [k for k in cfg if k.startswith("ms_")] == ["ms_" + rf["section"]]
+    assert (rf["bound"], rf["unit"], rf["peak"]) in (("hbm", "GB/s", 8000.0), ("mfma", "TFLOP/s", 2500.0))
+    assert 0 < rf["frac"] < 1 and rf["avg_launch_ms"] > 0
+    assert not detail.exists()
 
 
 def test_dump_outputs_of_the_last_timed_step(cuda, tmp_path):

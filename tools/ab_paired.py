@@ -14,7 +14,8 @@ T975 = {1: 12.706, 2: 4.303, 3: 3.182, 4: 2.776, 5: 2.571, 6: 2.447, 7: 2.365, 8
 
 def run(name, value, wl):
     env = dict(os.environ, **{name: str(value)})
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--no-extras", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--full", "--no-extras",
+                          "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, cwd=ROOT).stdout.strip().splitlines()[-1]
     d = json.loads(out)
     return d["ms_per_step"], d["config"].get("ms_per_step_over_whole_periods")

@@ -1,12 +1,12 @@
 # which HIP runtime calls sit between the last kernel of a step and the first of the next?  (GPU box)
+ROOT=$(cd "$(dirname "$0")/.." && pwd); GAP=$(mktemp -d)
 cd /tmp && export TMPDIR=/tmp
-rm -rf /root/repo/gpurun_out/gap && mkdir -p /root/repo/gpurun_out/gap
-rocprofv3 --hip-runtime-trace --kernel-trace --output-format csv -d /root/repo/gpurun_out/gap -o g -- python3 /root/repo/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras > /dev/null 2>&1
-cd /root/repo
-python - <<'PY'
-import csv, glob
-k = list(csv.DictReader(open(glob.glob("gpurun_out/gap/**/*kernel_trace.csv", recursive=True)[0])))
-a = list(csv.DictReader(open(glob.glob("gpurun_out/gap/**/*hip_api_trace.csv", recursive=True)[0])))
+rocprofv3 --hip-runtime-trace --kernel-trace --output-format csv -d "$GAP" -o g -- python3 "$ROOT/bench.py" --steps 6 --warmup 2 --full --no-cpu-baseline --no-extras > /dev/null 2>&1
+cd "$ROOT"
+GAP="$GAP" python - <<'PY'
+import csv, glob, os
+k = list(csv.DictReader(open(glob.glob(os.environ["GAP"] + "/**/*kernel_trace.csv", recursive=True)[0])))
+a = list(csv.DictReader(open(glob.glob(os.environ["GAP"] + "/**/*hip_api_trace.csv", recursive=True)[0])))
 k.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the last steady step boundary: an elementwise add kernel followed (> 20 us later) by k_idwt_fwd_pipe
 idx = [i for i in range(1, len(k)) if "k_idwt_fwd_pipe" in k[i]["Kernel_Name"] and "k_idwt_fwd_pipe" not in k[i - 1]["Kernel_Name"]]
@@ -23,3 +23,4 @@ for r in a:
     if ts - 400000 <= s <= ts + 20000:
         print(f'{(s - t0) / 1e3:9.1f} us  {(int(r["End_Timestamp"]) - s) / 1e3:7.1f} us  {r["Function"]}')
 PY
+rm -rf "$GAP"

@@ -3,8 +3,8 @@ between them (a new step starts when the previous launch of the kernel ended mor
 
 usage: python tools/kernel_per_step.py <dir with *_kernel_trace.csv> <kernel name substring> [out.csv] [gap_us=1500]
 Prints, and writes to out.csv, one row per step: index, launches, total microseconds, start (ms since the first launch).
-bench.py's phases in order: 4 dry-run steps, 16 set-up steps, W warm-up, K timed, min(K,16) instrumented, and (when the
-side work runs under the Adam pass) min(K,16) with it moved away; grid-refresh steps (every 16th) launch other variants.
+bench.py's phases in order: 4 dry-run steps, 32 set-up steps, W warm-up, K timed and, with --full, min(K,16) instrumented,
+min(K,8) with the side work moved away and 32 over whole periods; grid-refresh steps (every 16th) launch other variants.
 """
 import csv
 import glob
